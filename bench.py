@@ -56,7 +56,8 @@ The JSON line also carries
 
 Measurement switches (none changes what the timed region computes): ``--no-phases`` skips the serial hoists / step loop / vocoder / D2H
 timing after the timed region (profiler passes with counters on the batched workloads: DESIGN.md section 8, profiler note),
-``--no-clock-power`` the rocm-smi sampling pass, ``--no-cpu-baseline`` the oracle leg; ``--graph 0`` / ``--vocoder-graph 0`` launch eagerly,
+``--no-clock-power`` the rocm-smi sampling pass, ``--no-cpu-baseline`` the oracle leg, ``--dump-outputs DIR`` writes what the last timed step
+returned (see dump_outputs); ``--graph 0`` / ``--vocoder-graph 0`` launch eagerly,
 ``--skip-dead 1|2`` / ``--skip-masked 0`` select what a ragged batch's padding blocks cost (the attention half of a block
 skips them by default, exactly; the FF half on request), ``--xcd-runs 1`` is round 3's GEMM tile order, ``--attn-variant`` / ``--ln-fused`` / ``--ln-fold`` / ``--dual 0`` select the engine's
 non-default kernels and schedules (the A/Bs of DESIGN.md section 8).
@@ -335,6 +336,22 @@ def clock_power(step_fn, seconds: float = 4.0):
             "source": "rocm-smi --showclocks --showpower from a thread while the timed loop's work repeats (untimed)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """``--dump-outputs DIR``: what a caller of the timed path received from its LAST timed step, one ``DIR/<name>.npy`` per array in
+    float32 (rank 0's results).  The inputs and weights are seeded or come from the committed fixtures, so two builds run with the same
+    arguments can be compared output for output.  Every workload's outputs fit the 64 MB cap whole; exceeding it is an error."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs exceed the {DUMP_LIMIT_BYTES} byte cap")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
+
+
 def spawn_ranks(n: int) -> int:
     """Start the n ranks of a one-node data-parallel run ourselves (torchrun's environment contract, rendezvous on 127.0.0.1)."""
     with socket.socket() as s:
@@ -418,9 +435,11 @@ def run_job(a, w, model, vocoder, rank, world, dist, comm_device, device, bcast)
 
     for _ in range(max(a.warmup, 1)):
         once()
-    runs = [once() for _ in range(max(a.steps, 1))]
+    runs = [once() for _ in range(a.steps)]
     times = [r[0] for r in runs]
     host = runs[-1][1]
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"wav": host.numpy()})       # [64 utterances, samples]: the waveforms the job returns on rank 0's host
     mine_t = torch.tensor([[t["scatter_ms"], t["compute_ms"], t["gather_ms"], t["job_ms"]] for t in times], dtype=torch.float64).mean(0)
     every = [mine_t]
     if dist and world > 1:
@@ -439,7 +458,7 @@ def run_job(a, w, model, vocoder, rank, world, dist, comm_device, device, bcast)
     job_ms = float(every[0][3])
     audio = U * HOP * (L - 1) / SR
     return {"metric": f"audio-seconds/sec @24kHz (NFE={nfe}, CFG on): sharded JOB", "value": audio / (job_ms * 1e-3), "unit": "audio-seconds/sec",
-            "n_gpus": world, "steps": max(a.steps, 1), "warmup": max(a.warmup, 1), "ms_per_step": job_ms, "higher_is_better": True, "scaling": "strong",
+            "n_gpus": world, "steps": a.steps, "warmup": max(a.warmup, 1), "ms_per_step": job_ms, "higher_is_better": True, "scaling": "strong",
             "vs_baseline": None, "dtype": "fp8" if a.fp8 else "bf16", "data": "synthetic",
             "config": {"workload": f"BASELINE configs[3] as a job: {U} utterances of 4 s ref + 8 s target (F={F_}, N={N}) owned by rank 0, dealt to "
                                    f"{world} rank(s) ({U // world} per rank, run as batches of {MB}), NFE={nfe}, CFG={CFG}, waveforms gathered on rank 0's host",
@@ -493,7 +512,11 @@ def main():
     ap.add_argument("--skip-masked", type=int, default=-1, help="engine option skip_masked (-1 = engine default 1: the attention half of every block "
                     "skips a ragged batch's padding blocks -- exact, the reference zeroes that half's output there; 0 = compute them, for A/B runs)")
     ap.add_argument("--no-clock-power", action="store_true", help="skip the rocm-smi clock / power sampling pass (profiler runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one returned (the mel of "
+                    "every sample and the waveforms; rank 0) as DIR/<name>.npy, float32")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(spawn_ranks(a.gpus))
@@ -656,6 +679,13 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:      # before anything below runs the path again: the mel [B, N, 100] and the waveforms of the last timed step
+        outs = {"mel": last["out"].detach().cpu().numpy()}
+        if w["vocode"] == "generated":
+            outs["wav"] = host_wav[0].numpy()                                       # [B, samples]: one decode of the whole batch
+        else:
+            outs.update({f"wav_{i}": hw.numpy() for i, hw in enumerate(host_wav)})  # [1, samples] per waveform, in vocode_segments order
+        dump_outputs(a.dump_outputs, outs)
     per_rank_ms = [1e3 * elapsed / max(a.steps, 1)]
     if dist:
         mine = torch.tensor([elapsed], device=comm_device, dtype=torch.float64)

@@ -10,8 +10,11 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "lib", "liblemas_hip.so")
-TEST_LIB_PATH = os.path.join(_HERE, "lib", "liblemas_hip_test.so")
+# LEMAS_LIB_DIR: load the pair from another directory -- the tests of the measurement build (lemas_tts_amd/build.py) run in a child
+# process pointed at lib/measurement/
+_LIBDIR = os.environ.get("LEMAS_LIB_DIR") or os.path.join(_HERE, "lib")
+LIB_PATH = os.path.join(_LIBDIR, "liblemas_hip.so")
+TEST_LIB_PATH = os.path.join(_LIBDIR, "liblemas_hip_test.so")
 
 _lib = None
 _testlib = None

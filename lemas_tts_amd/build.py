@@ -5,6 +5,10 @@ one copy of every kernel) in-tree with hipcc for gfx950 (cross-compiles without 
     python -m lemas_tts_amd.build            # incremental
     python -m lemas_tts_amd.build --force
 
+build_library(measurement=True) builds the same two libraries with -DLEMAS_MEASUREMENT_BUILD into lib/measurement/ (objects in
+csrc/_build_measurement/): the measured experiments the product build leaves out.  The tests of those experiments load that pair in a
+child process (LEMAS_LIB_DIR, tests/conftest.py); the product path never loads it.
+
 The .so is git-ignored but travels to the GPU box with the gpurun snapshot.
 """
 from __future__ import annotations
@@ -20,6 +24,7 @@ OBJ = os.path.join(CSRC, "_build")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "liblemas_hip.so")
 TEST_LIB = os.path.join(LIBDIR, "liblemas_hip_test.so")
+MEASUREMENT_LIBDIR = os.path.join(LIBDIR, "measurement")
 TEST_ONLY = {"engine_ktests.hip", "attention_q64.hip"}     # sources that go into the test library, not the product (test entry points,
                                                            # measurement-only kernels)
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
@@ -40,12 +45,12 @@ def _headers_mtime():
     return max(os.path.getmtime(h) for h in hs)
 
 
-def _compile(src: str, force: bool) -> str:
-    obj = os.path.join(OBJ, src[:-4] + ".o")
+def _compile(src: str, force: bool, objdir: str = OBJ, extra=()) -> str:
+    obj = os.path.join(objdir, src[:-4] + ".o")
     spath = os.path.join(CSRC, src)
     if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(spath), _headers_mtime()):
         return obj
-    cmd = [HIPCC, *FLAGS, "-c", spath, "-o", obj]
+    cmd = [HIPCC, *FLAGS, *extra, "-c", spath, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")
@@ -61,20 +66,24 @@ def _link(out: str, objs, extra=()) -> None:
         raise RuntimeError(f"link failed:\n{r.stdout}\n{r.stderr}")
 
 
-def build_library(force: bool = False) -> str:
-    os.makedirs(OBJ, exist_ok=True)
-    os.makedirs(LIBDIR, exist_ok=True)
+def build_library(force: bool = False, measurement: bool = False) -> str:
+    objdir = OBJ + "_measurement" if measurement else OBJ
+    libdir = MEASUREMENT_LIBDIR if measurement else LIBDIR
+    extra = ["-DLEMAS_MEASUREMENT_BUILD"] if measurement else []
+    lib, test_lib = os.path.join(libdir, os.path.basename(LIB)), os.path.join(libdir, os.path.basename(TEST_LIB))
+    os.makedirs(objdir, exist_ok=True)
+    os.makedirs(libdir, exist_ok=True)
     srcs = _sources()
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as ex:
-        objs = dict(zip(srcs, ex.map(lambda s: _compile(s, force), srcs)))
+        objs = dict(zip(srcs, ex.map(lambda s: _compile(s, force, objdir, extra), srcs)))
     prod = [o for s, o in objs.items() if s not in TEST_ONLY]
     test = [o for s, o in objs.items() if s in TEST_ONLY]
-    if force or not os.path.exists(LIB) or any(os.path.getmtime(o) > os.path.getmtime(LIB) for o in prod):
-        _link(LIB, prod)
-    if force or not os.path.exists(TEST_LIB) or os.path.getmtime(LIB) > os.path.getmtime(TEST_LIB) or \
-            any(os.path.getmtime(o) > os.path.getmtime(TEST_LIB) for o in test):
-        _link(TEST_LIB, test, ["-L", LIBDIR, "-llemas_hip", "-Wl,-rpath,$ORIGIN"])
-    return LIB
+    if force or not os.path.exists(lib) or any(os.path.getmtime(o) > os.path.getmtime(lib) for o in prod):
+        _link(lib, prod)
+    if force or not os.path.exists(test_lib) or os.path.getmtime(lib) > os.path.getmtime(test_lib) or \
+            any(os.path.getmtime(o) > os.path.getmtime(test_lib) for o in test):
+        _link(test_lib, test, ["-L", libdir, "-llemas_hip", "-Wl,-rpath,$ORIGIN"])
+    return lib
 
 
 def build_c_client() -> str:
@@ -95,4 +104,5 @@ def build_c_client() -> str:
 
 if __name__ == "__main__":
     print(build_library(force="--force" in sys.argv))
+    print(build_library(force="--force" in sys.argv, measurement=True))
     print(build_c_client())

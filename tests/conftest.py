@@ -1,4 +1,6 @@
+import functools
 import os
+import subprocess
 import sys
 
 import pytest
@@ -26,5 +28,22 @@ def measurement_build() -> bool:
     return bool(_lib.testlib().lemas_k_build_flags() & 1)
 
 
-needs_measurement_build = pytest.mark.skipif("not __import__('conftest').measurement_build()",
-                                             reason="measurement-only code: build with LEMAS_EXTRA_HIPCC_FLAGS=-DLEMAS_MEASUREMENT_BUILD")
+MEASUREMENT_LIBDIR = os.path.join(ROOT, "lemas_tts_amd", "lib", "measurement")
+
+
+def needs_measurement_build(test):
+    """Measurement-only code (build() makes that pair of libraries in lemas_tts_amd/lib/measurement/): in a process holding the product
+    libraries the test runs in a child pytest pointed at the measurement pair (one library pair per process: they export the same
+    symbols); in a measurement process -- that child, or a tree built with -DLEMAS_MEASUREMENT_BUILD -- it runs as it is."""
+    @functools.wraps(test)
+    def run(*args, **kwargs):
+        if measurement_build():
+            return test(*args, **kwargs)
+        if not os.path.exists(os.path.join(MEASUREMENT_LIBDIR, "liblemas_hip_test.so")):
+            pytest.fail("lemas_tts_amd/lib/measurement/ is missing: run build()")
+        nodeid = os.environ["PYTEST_CURRENT_TEST"].rsplit(" ", 1)[0]
+        r = subprocess.run([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", nodeid], cwd=ROOT, capture_output=True,
+                           text=True, env=dict(os.environ, LEMAS_LIB_DIR=MEASUREMENT_LIBDIR))
+        print(r.stdout[-3000:])
+        assert r.returncode == 0 and " passed" in r.stdout and "skipped" not in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+    return run

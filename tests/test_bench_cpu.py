@@ -78,3 +78,24 @@ def test_frontend_bench_counts_the_encoder_flops_of_the_weights_it_loads():
                 want += 2 * T * n
         assert fb.ecapa_flops(arch, T) == want, (fb.ecapa_flops(arch, T), want)
     assert fb.ecapa_flops(ProsodyArch(), 998) == 9562013696     # the figure in DESIGN.md section 3 / profiles/r06/r06fk_frontend_bench.json
+
+
+def test_dump_outputs_writes_float32_npy_and_keeps_the_cap(tmp_path):
+    """``--dump-outputs DIR``: one DIR/<name>.npy per output array, float32; more than 64 MB in all is refused, not truncated"""
+    import numpy as np
+    import bench
+    mel = np.arange(2 * 3 * 100, dtype=np.float64).reshape(2, 3, 100)
+    bench.dump_outputs(str(tmp_path / "d"), {"mel": mel, "wav": np.ones((2, 512), np.float32)})
+    got = np.load(tmp_path / "d" / "mel.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 3, 100) and np.array_equal(got, mel.astype(np.float32))
+    assert np.load(tmp_path / "d" / "wav.npy").shape == (2, 512)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)})
+    assert not (tmp_path / "big").exists()
+
+
+def test_steps_must_be_a_real_count():
+    """``--steps`` is the number of timed steps: 0 is refused at the command line (before any GPU is touched)"""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr
