@@ -99,6 +99,54 @@ int lemas_k_build_flags(void);
 int lemas_k_bench(const char* what, int32_t M, int32_t N, int32_t K, int32_t iters, int32_t variant, double* avg_us);
 
 
+/* ---- the exact-fp32 path, one production kernel per entry point (csrc/gemm_f32.hip, prosody_kernels.hip, fft_kernels.hip,
+ * aux_kernels.hip, mdx_kernels.hip).  Each goes straight to its launcher: a refusal returns that launcher's error, nothing is launched. */
+/* mirrors the kernel's own parameter block field by field (csrc/common.h GemmF32Params); Wv / biasv are DEVICE arrays of nbatch device
+ * pointers, out_bstride is in floats */
+typedef struct lemas_k_gemm_f32_args {
+  const float* A; int32_t lda;
+  const float* W; int32_t ldw;
+  const float* bias;
+  float* out; int32_t ldc;
+  int32_t M, N, K;
+  const float* res; int32_t ldres;
+  const float* colscale;
+  const float* add;
+  const uint8_t* rowmask;
+  int32_t nbatch;
+  const float* const* Wv;
+  const float* const* biasv;
+  int64_t out_bstride;
+  const float* rowscale; const float* rowshift;
+  int32_t rows_per_ch, nch;
+} lemas_k_gemm_f32_args;
+/* epi: the F32_* epilogue number (0 bias, 1 gelu-erf, 2 silu, 3 res + colscale * (.), 4 add2, 5 relu, 6 sigmoid, 7 rowaff-relu, 8 rowaff-relu + res) */
+int lemas_k_gemm_f32_ex(int32_t epi, const lemas_k_gemm_f32_args* args, void* stream);
+/* the one-row Linear: out[N] = act(A[K] . W[N, ldw]^T + bias); epi 0 / 5 / 6 only */
+int lemas_k_gemv_f32(int32_t epi, const float* A, const float* W, int32_t ldw, const float* bias, float* out, int32_t N, int32_t K, void* stream);
+/* the FFT plan of length n: radices (host int32 [cap]) in stage order; returns their count, or -1 when the length is refused */
+int lemas_k_fft_plan(int32_t n, int32_t* radices, int32_t cap);
+/* frames [rows][n] -> spec [rows][ld] = [re(0..n/2) | im(0..n/2) | zeros]; and back: frames = window / n * irfft(spec) */
+int lemas_k_rfft_rows(int32_t n, const float* frames, int32_t rows, float* spec, int32_t ld, void* stream);
+int lemas_k_irfft_rows(int32_t n, const float* spec, int32_t ld, int32_t rows, const float* window, float* frames, void* stream);
+/* one Res2Net chunk: out = LayerNorm(relu(conv1d_{3 taps, dil}(x + add) + bias)), 64 -> 64 channels, time-major rows; W = the
+ * reference's [64][64][3] weight (re-laid here) */
+int lemas_k_res2net_step(const float* x, int32_t ldx, const float* add, int32_t ldadd, int32_t T, int32_t dil, const float* W, const float* bias,
+                         const float* lnw, const float* lnb, float eps, float* out, int32_t ldo, void* stream);
+/* depthwise conv k = 7 (padding 3 per sample) + LayerNorm(eps 1e-6) of x [B][N][C]; w [C][7] */
+int lemas_k_dwconv7_ln(const float* x, const float* w, const float* bias, const float* lnw, const float* lnb, float* out, int32_t B, int32_t N,
+                       int32_t C, void* stream);
+/* per-column mean / std (uniform weights) and attentive statistics pooling (softmax over time of att) of x [T][ldx] */
+int lemas_k_col_stats(const float* x, int32_t ldx, int32_t T, int32_t C, float eps, float* mean, float* stdv, void* stream);
+int lemas_k_softmax_pool(const float* att, int32_t lda, const float* x, int32_t ldx, int32_t T, int32_t C, float eps, float* mean, float* stdv,
+                         void* stream);
+/* LayerNorm over the C channels of each of T rows, optional tanh */
+int lemas_k_ln_rows(const float* x, int32_t ldx, int32_t T, int32_t C, const float* w, const float* b, float eps, int32_t act_tanh, float* out,
+                    int32_t ldo, void* stream);
+/* GroupNorm(2, C) + relu of x [B * C * T rows][ld] (cols valid columns); mode 1: * other, 2: + other */
+int lemas_k_mdx_groupnorm(const float* x, int32_t ld, int32_t cols, int32_t B, int32_t C, int32_t T, const float* gamma, const float* beta, float eps,
+                          const float* other, int32_t mode, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,15 @@ class SampleArgs(C.Structure):
         self.struct_size = C.sizeof(SampleArgs)      # ABI 200: checked by the library
 
 
+class GemmF32Args(C.Structure):
+    """lemas_k_gemm_f32_args (include/lemas_hip_test.h): the exact-fp32 GEMM's parameter block, for lemas_k_gemm_f32_ex."""
+    _fields_ = [("A", C.c_void_p), ("lda", C.c_int32), ("W", C.c_void_p), ("ldw", C.c_int32), ("bias", C.c_void_p),
+                ("out", C.c_void_p), ("ldc", C.c_int32), ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+                ("res", C.c_void_p), ("ldres", C.c_int32), ("colscale", C.c_void_p), ("add", C.c_void_p), ("rowmask", C.c_void_p),
+                ("nbatch", C.c_int32), ("Wv", C.c_void_p), ("biasv", C.c_void_p), ("out_bstride", C.c_int64),
+                ("rowscale", C.c_void_p), ("rowshift", C.c_void_p), ("rows_per_ch", C.c_int32), ("nch", C.c_int32)]
+
+
 class LemasError(RuntimeError):
     pass
 
@@ -159,7 +168,7 @@ def testlib():
     if not os.path.exists(TEST_LIB_PATH):
         raise LemasError(f"{TEST_LIB_PATH} is missing: build it with `python -m lemas_tts_amd.build`")
     T = C.CDLL(TEST_LIB_PATH)
-    vp, i32 = C.c_void_p, C.c_int32
+    vp, i32, f32 = C.c_void_p, C.c_int32, C.c_float
     sig = {
         "lemas_k_linear_bf16": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
         "lemas_k_linear_f32": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
@@ -178,6 +187,17 @@ def testlib():
         "lemas_k_gemm_gate_ln": (C.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
         "lemas_k_ln_fold_pair": (C.c_int, [i32, i32, i32] + [vp] * 12 + [i32] * 6 + [vp]),
         "lemas_k_bench": (C.c_int, [C.c_char_p, i32, i32, i32, i32, i32, C.POINTER(C.c_double)]),
+        "lemas_k_gemm_f32_ex": (C.c_int, [i32, C.POINTER(GemmF32Args), vp]),
+        "lemas_k_gemv_f32": (C.c_int, [i32, vp, vp, i32, vp, vp, i32, i32, vp]),
+        "lemas_k_fft_plan": (C.c_int, [i32, C.POINTER(i32), i32]),
+        "lemas_k_rfft_rows": (C.c_int, [i32, vp, i32, vp, i32, vp]),
+        "lemas_k_irfft_rows": (C.c_int, [i32, vp, i32, i32, vp, vp, vp]),
+        "lemas_k_res2net_step": (C.c_int, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, f32, vp, i32, vp]),
+        "lemas_k_dwconv7_ln": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+        "lemas_k_col_stats": (C.c_int, [vp, i32, i32, i32, f32, vp, vp, vp]),
+        "lemas_k_softmax_pool": (C.c_int, [vp, i32, vp, i32, i32, i32, f32, vp, vp, vp]),
+        "lemas_k_ln_rows": (C.c_int, [vp, i32, i32, i32, vp, vp, f32, i32, vp, i32, vp]),
+        "lemas_k_mdx_groupnorm": (C.c_int, [vp, i32, i32, i32, i32, i32, vp, vp, f32, vp, i32, vp, vp]),
     }
     _bind(T, sig)
     _testlib = _WithTests(prod, T)
@@ -198,6 +218,8 @@ EXPORTED = [      # include/lemas_hip.h: the product library
 EXPORTED_TEST = [  # include/lemas_hip_test.h: the test library
     "lemas_k_linear_bf16", "lemas_k_linear_f32", "lemas_k_attention", "lemas_k_attention_variant", "lemas_k_ln_mod", "lemas_k_convpos", "lemas_k_bench", "lemas_k_gemm_epi",
     "lemas_k_gemm_gate_ln", "lemas_k_ln_fold_pair", "lemas_k_timeline", "lemas_k_build_flags", "lemas_k_mx_quant", "lemas_k_w_quant_f8", "lemas_k_ln_mod_f8", "lemas_k_outlier_rows", "lemas_k_linear_f8",
+    "lemas_k_gemm_f32_ex", "lemas_k_gemv_f32", "lemas_k_fft_plan", "lemas_k_rfft_rows", "lemas_k_irfft_rows", "lemas_k_res2net_step",
+    "lemas_k_dwconv7_ln", "lemas_k_col_stats", "lemas_k_softmax_pool", "lemas_k_ln_rows", "lemas_k_mdx_groupnorm",
 ]
 
 

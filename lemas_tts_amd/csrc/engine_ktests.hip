@@ -735,3 +735,132 @@ extern "C" int lemas_k_bench(const char* what, int32_t M, int32_t N, int32_t K, 
   return rc;
 }
 
+
+// ---- exact-fp32 path, one kernel per entry point (tests/test_gpu_15_f32_kernels.py): each goes straight to its launcher, so a refusal
+// comes back as the launcher's own error code, and synchronises before returning ------------------------------------------------------
+
+int lemas_k_gemm_f32_ex(int32_t epi, const lemas_k_gemm_f32_args* a, void* stream) {
+  if (!a) { set_error("lemas_k_gemm_f32_ex: null arguments"); return LEMAS_E_ARG; }
+  hipStream_t s = (hipStream_t)stream;
+  GemmF32Params p{};
+  p.A = a->A; p.lda = a->lda; p.W = a->W; p.ldw = a->ldw; p.bias = a->bias; p.out = a->out; p.ldc = a->ldc;
+  p.M = a->M; p.N = a->N; p.K = a->K;
+  p.res = a->res; p.ldres = a->ldres; p.colscale = a->colscale; p.add = a->add; p.rowmask = a->rowmask;
+  p.nbatch = a->nbatch; p.Wv = a->Wv; p.biasv = a->biasv; p.out_bstride = (size_t)a->out_bstride;
+  p.rowscale = a->rowscale; p.rowshift = a->rowshift; p.rows_per_ch = a->rows_per_ch; p.nch = a->nch;
+  HIP_TRY(launch_gemm_f32(epi, p, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int lemas_k_gemv_f32(int32_t epi, const float* A, const float* W, int32_t ldw, const float* bias, float* out, int32_t N, int32_t K, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  GemmF32Params p{};
+  p.A = A; p.lda = K; p.W = W; p.ldw = ldw; p.bias = bias; p.out = out; p.ldc = N; p.M = 1; p.N = N; p.K = K;
+  HIP_TRY(launch_gemv_f32(epi, p, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int lemas_k_fft_plan(int32_t n, int32_t* radices, int32_t cap) {
+  FftPlan plan{};
+  if (!fft_plan_make(n, &plan)) return -1;
+  for (int i = 0; i < plan.nrad && i < cap; ++i) radices[i] = plan.rad[i];
+  return plan.nrad;
+}
+
+namespace {
+// the plan, the LDS opt-in and the twiddle table exp(-2 pi i t / n) (double precision on the host) exactly as lemas_stft_create makes them
+int fft_setup(int n, Scratch& sc, FftPlan* plan, float** tw, hipStream_t s) {
+  if (!fft_plan_make(n, plan)) { set_error("fft: length %d has no plan", n); return LEMAS_E_ARG; }
+  HIP_TRY(fft_kernels_init(*plan));
+  std::vector<float> t((size_t)2 * n);
+  for (int i = 0; i < n; ++i) {
+    const double a = -2.0 * M_PI * (double)i / (double)n;
+    t[2 * i] = (float)std::cos(a);
+    t[2 * i + 1] = (float)std::sin(a);
+  }
+  *tw = sc.get<float>(t.size());
+  if (!*tw) { set_error("fft: out of memory"); return LEMAS_E_STATE; }
+  HIP_TRY(hipMemcpyAsync(*tw, t.data(), t.size() * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+}  // namespace
+
+int lemas_k_rfft_rows(int32_t n, const float* frames, int32_t rows, float* spec, int32_t ld, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  Scratch sc;
+  FftPlan plan{};
+  float* tw = nullptr;
+  RC_TRY(fft_setup(n, sc, &plan, &tw, s));
+  HIP_TRY(launch_rfft_rows(plan, tw, frames, rows, spec, ld, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int lemas_k_irfft_rows(int32_t n, const float* spec, int32_t ld, int32_t rows, const float* window, float* frames, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  Scratch sc;
+  FftPlan plan{};
+  float* tw = nullptr;
+  RC_TRY(fft_setup(n, sc, &plan, &tw, s));
+  HIP_TRY(launch_irfft_rows(plan, tw, spec, ld, rows, window, frames, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int lemas_k_res2net_step(const float* x, int32_t ldx, const float* add, int32_t ldadd, int32_t T, int32_t dil, const float* W, const float* bias,
+                         const float* lnw, const float* lnb, float eps, float* out, int32_t ldo, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  Scratch sc;
+  float* img = sc.get<float>(res2net_weight_image_floats());
+  if (!img) { set_error("res2net_step: out of memory"); return LEMAS_E_STATE; }
+  HIP_TRY(launch_res2net_weight_image(W, img, s));
+  HIP_TRY(launch_res2net_step(x, ldx, add, ldadd, T, dil, img, bias, lnw, lnb, eps, out, ldo, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int lemas_k_dwconv7_ln(const float* x, const float* w, const float* bias, const float* lnw, const float* lnb, float* out, int32_t B, int32_t N,
+                       int32_t C, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(launch_dwconv7_ln(x, w, bias, lnw, lnb, out, B, N, C, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int lemas_k_col_stats(const float* x, int32_t ldx, int32_t T, int32_t C, float eps, float* mean, float* stdv, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(launch_col_stats(x, ldx, T, C, eps, mean, stdv, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int lemas_k_softmax_pool(const float* att, int32_t lda, const float* x, int32_t ldx, int32_t T, int32_t C, float eps, float* mean, float* stdv,
+                         void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(launch_softmax_pool(att, lda, x, ldx, T, C, eps, mean, stdv, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int lemas_k_ln_rows(const float* x, int32_t ldx, int32_t T, int32_t C, const float* w, const float* b, float eps, int32_t act_tanh, float* out,
+                    int32_t ldo, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(launch_ln_rows(x, ldx, T, C, w, b, eps, act_tanh, out, ldo, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int lemas_k_mdx_groupnorm(const float* x, int32_t ld, int32_t cols, int32_t B, int32_t C, int32_t T, const float* gamma, const float* beta, float eps,
+                          const float* other, int32_t mode, float* out, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  Scratch sc;
+  double* part = sc.get<double>((size_t)(B > 0 ? B : 1) * 2 * 64 * 2);
+  float* stats = sc.get<float>((size_t)(B > 0 ? B : 1) * 2 * 2);
+  if (!part || !stats) { set_error("mdx_groupnorm: out of memory"); return LEMAS_E_STATE; }
+  HIP_TRY(launch_mdx_groupnorm(x, ld, cols, B, C, T, gamma, beta, eps, other, mode, out, part, stats, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
