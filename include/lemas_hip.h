@@ -153,7 +153,11 @@ int lemas_dit_set_option(lemas_dit* m, const char* key, int64_t value);
  * EVERY GEMM site (2.9e-4 mel-MSE at full depth / NFE 32 against the 1e-4 target; no single site stays under it with margin), so fp8 does
  * not ship for such weights.  0 = run fp8 regardless; round 5's mixed-precision decomposition, option "fp8_outlier_mode", met the target
  * but ran slower than this fallback and lives in measurement builds only since round 6), "fp8_sites" (mask of the GEMM sites of a block that take fp8 operands when
- * "fp8" = 1: 1 QKV, 2 out-projection, 4 FF1, 8 FF2; default 15).
+ * "fp8" = 1: 1 QKV, 2 out-projection, 4 FF1, 8 FF2; default 15), "ode_method" (the solver of the reference's odeint_kwargs["method"],
+ * torchdiffeq 0.2.4's fixed-grid arithmetic: 0 = euler, default; 1 = midpoint, 2 evaluations per step; 2 = rk4, the 3/8 rule, 4 evaluations
+ * per step.  A step's evaluations run at their own times, so the time / AdaLN tables and the CFG scale cover E = steps x evaluations rows,
+ * the captured graph is one evaluation and solve() replays it E times; the trajectory keeps one row per step.  A change drops the prepared
+ * state and the captured graphs: it takes effect at the next prepare() / sample(), and solve() / forward() return LEMAS_E_STATE until then).
  * counters since creation, for tools and tests: "graph_captures", "graph_instantiates", "graph_updates", "graph_update_failures",
  * "graph_evictions", "graph_buckets", "fp8_outlier_channels" (residual channels flagged by the guard; -1 before the first fp8 prepare),
  * "fp8_gemms_kept_bf16" (GEMMs per DiT block that run on bf16 operands while "fp8" = 1: 0; 4 when the guard tripped) */
@@ -161,12 +165,13 @@ int lemas_dit_get_stat(lemas_dit* m, const char* key, int64_t* value);
 /* synchronises the device and returns 0, or LEMAS_E_STATE when a device-side wait of this engine gave up (fused LayerNorm tail):
  * every result since then is invalid and prepare() / solve() refuse to run */
 int lemas_dit_health(lemas_dit* m);
-/* full sampler: hoists + NFE Euler steps (+ final where) */
+/* full sampler: hoists + NFE steps of the "ode_method" solver (+ final where) */
 int lemas_dit_sample(lemas_dit* m, const lemas_sample_args* a, void* stream);
 /* split form: prepare() runs the per-utterance hoists, solve() the step loop on the prepared state */
 int lemas_dit_prepare(lemas_dit* m, const lemas_sample_args* a, void* stream);
 int lemas_dit_solve(lemas_dit* m, const lemas_sample_args* a, void* stream);
-/* one DiT forward at step index k of the prepared grid: x device [B,N,mel] -> pred device [BB*N, mel]
+/* one DiT forward at EVALUATION index k of the prepared grid, k in [0, steps x evaluations per step of "ode_method") (euler: the step
+ * index; midpoint / rk4: stage k % 2 / k % 4 of step k / 2 / k / 4, at that stage's time): x device [B,N,mel] -> pred device [BB*N, mel]
  * (BB = 2B with CFG: conditional rows first, then unconditional) */
 int lemas_dit_forward(lemas_dit* m, const float* x, int32_t step_index, float* pred, void* stream);
 /* per-kernel-class timings collected while option "profile" = 1: fills up to `cap` entries, returns the count.

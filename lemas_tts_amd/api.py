@@ -105,6 +105,8 @@ class TTS:
                  vocoder_local_path=None, use_prosody_encoder=False, prosody_cfg_path="", prosody_ckpt_path="",
                  device=None, hf_cache_dir=None, frontend=None, *, state_dict=None, vocoder_state_dict=None,
                  vocab_char_map=None):
+        from .model.cfm import ode_method_code
+        ode_method_code(dict(method=ode_method))     # euler / midpoint / rk4: refused here, before the vocoder and the model load
         cfg = load_arch_config(model)                                   # api.py:99-105
         self.mel_spec_type = cfg["mel_spec"]["mel_spec_type"]
         self.target_sample_rate = cfg["mel_spec"]["target_sample_rate"]

@@ -382,6 +382,14 @@ hipError_t launch_convpos(const ConvPosParams& p, hipStream_t s);
 hipError_t launch_cfg_euler(float* y, const float* pred /*[2B*N,100] cond rows then uncond rows*/, int rows, int cols,
                             const float* dt_tab, const float* cfg_tab, int* step_idx, float* traj, int use_cfg, hipStream_t s);
 
+// one evaluation of a fixed-grid midpoint / rk4 solve (engine option "ode_method"): which stage, the step's dt, the stage's coefficient
+enum OdeStageKind : int { ODE_MID0 = 0, ODE_MID1 = 1, ODE_RK0 = 2, ODE_RK1 = 3, ODE_RK2 = 4, ODE_RK3 = 5 };
+struct OdeStage { int kind; float dt; float c; int pad; };
+// CFG + clamp at the evaluation's cfg_tab row, then the stage of stages[step] (norm_elementwise.hip ode_stage_kernel); step counter++.
+// base / k1..k3: [rows, cols] fp32 (k1..k3 are read / written by the rk4 stages only)
+hipError_t launch_ode_stage(float* y, const float* pred, int rows, int cols, const OdeStage* stages, const float* cfg_tab, int* step_idx,
+                            float* base, float* k1, float* k2, float* k3, int use_cfg, int n_cus, hipStream_t s);
+
 // ---- fp32 (exact) GEMM on f32 MFMA for the once-per-utterance and vocoder work --------------------
 enum F32Epi : int {
   F32_BIAS = 0,        // out = acc + bias

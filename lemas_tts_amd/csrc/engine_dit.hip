@@ -12,6 +12,9 @@
 //               reference runs the two branches sequentially, cfm.py:393-417) + fused CFG/clamp/Euler update.
 //               The step's ~165 launches are captured once per shape into a hipGraph and replayed; the step
 //               index lives in device memory so the same graph serves every step.
+//   option "ode_method" (1 = midpoint, 2 = rk4; torchdiffeq 0.2.4's fixed-grid solvers): a step is `stages` (2 / 4) network
+//               EVALUATIONS at their own times.  The tables above, the CFG scale and the device counter then run over the
+//               E = S * stages evaluations, the captured graph is one evaluation (forward + ode_stage_kernel), launched E times.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -22,9 +25,9 @@
 namespace lemas {
 
 enum ProfClass { PC_INPROJ, PC_CONVPOS, PC_LN, PC_GEMM_QKV, PC_GEMM_QK, PC_GEMM_V, PC_ATTN, PC_GEMM_OUT, PC_GEMM_FF1, PC_GEMM_FF2, PC_GEMM_FINAL,
-                 PC_CFG_EULER, PC_COUNT };
+                 PC_CFG_EULER, PC_ODE_STAGE, PC_COUNT };
 static const char* kProfNames[PC_COUNT] = {"inproj_f32", "convpos", "ln_mod", "gemm_qkv_fused", "gemm_qk_rope", "gemm_v_t", "attention", "gemm_attn_out",
-                                           "gemm_ff1_gelu", "gemm_ff2", "gemm_proj_out", "cfg_euler"};
+                                           "gemm_ff1_gelu", "gemm_ff2", "gemm_proj_out", "cfg_euler", "ode_stage"};
 
 struct BlockW {
   DevBuf wqkv, wo, w1, w2;  // bf16
@@ -168,10 +171,17 @@ struct lemas_dit {
   int pitch = 0;  // rows per sample in the activation row space: N rounded up to 128 (tiles never straddle samples)
   bool use_cfg = true, has_len = false, prepared = false;
   std::vector<float> tgrid_cached;
+  // option "ode_method": 0 = euler (torchdiffeq's fixed-grid Euler, the reference's shipped choice), 1 = midpoint, 2 = rk4 (the 3/8 rule).
+  // The prepared state holds E = S * stages evaluations; `tab_method` is the method the cached time / AdaLN tables were built for
+  int ode_method = 0, tab_method = -1, E = 0;
+  static int ode_stages(int m) { return m == 1 ? 2 : m == 2 ? 4 : 1; }
+  std::vector<float> h_te;                 // evaluation times (ode_method != 0)
+  std::vector<OdeStage> h_ode;
   int rope_n = 0;
   std::vector<float> h_dt, h_cfg, h_t;
 
   DevBuf d_step, d_dt, d_cfg, d_t, d_tab, d_rope_cos, d_rope_sin, d_len, d_live;
+  DevBuf d_ode, d_ybase, d_k1, d_k2, d_k3;                // ode_method != 0: per-evaluation stage rows, y0 of the step, rk4 slopes
   DevBuf d_sin, d_h1, d_temb, d_st;                       // time path scratch
   DevBuf d_cond_eff, d_step_cond, d_pm, d_pt;             // conditioning
   DevBuf d_te, d_rowmask, d_t1, d_t2, d_t3, d_gx, d_ct;   // text embedding scratch
@@ -210,7 +220,7 @@ struct lemas_dit {
             &d_rope_sin, &d_len, &d_live, &d_sin, &d_h1, &d_temb, &d_st, &d_cond_eff, &d_step_cond, &d_pm, &d_pt, &d_te,
             &d_rowmask, &d_t1, &d_t2, &d_t3, &d_gx, &d_ct, &d_pconst, &d_y, &d_xres, &d_hbf, &d_q, &d_k, &d_vt, &d_q8, &d_k8, &d_qs8, &d_ks8,
             &d_abf, &d_ff, &d_cmid, &d_pred, &d_h8, &d_hmx, &d_a8, &d_amx, &d_ff8, &d_ffmx, &d_lncnt, &d_lnpart,
-            &d_foldA, &d_foldtmp, &d_foldsites, &d_foldparams, &d_zero, &d_flagged};
+            &d_foldA, &d_foldtmp, &d_foldsites, &d_foldparams, &d_zero, &d_flagged, &d_ode, &d_ybase, &d_k1, &d_k2, &d_k3};
   }
   static std::vector<DevBuf*> block_bufs(BlockW& b) {
     return {&b.wqkv, &b.wo, &b.w1, &b.w2, &b.bqkv, &b.wqkv8, &b.wo8, &b.w18, &b.w28, &b.sqkv, &b.so, &b.s1, &b.s2, &b.wqkvq, &b.woq, &b.w1q, &b.w2q,
@@ -563,26 +573,64 @@ int lemas_dit::finalize() {
 }
 
 // time MLP + AdaLN vectors for every step, dt / cfg_t tables, rotary table
+// Evaluation grid of the higher-order fixed-grid solvers (torchdiffeq 0.2.4 FixedGridODESolver.integrate + fixed_grid.Midpoint +
+// rk_common.rk4_alt_step_func; all fp32 since the grid is fp32), step k from t0 = t[k] to t1 = t[k+1], dt = t1 - t0, y1 = y0 + dy:
+//   midpoint  half_dt = 0.5 * dt;  f0 = f(t0, y0);  y_mid = y0 + f0 * half_dt;  dy = dt * f(t0 + half_dt, y_mid)
+//   rk4       k1 = f(t0, y0);  k2 = f(t0 + dt * (1/3), y0 + dt * k1 * (1/3));  k3 = f(t0 + dt * (2/3), y0 + dt * (k2 - k1 * (1/3)));
+//             k4 = f(t1, y0 + dt * (k1 - k2 + k3));  dy = (k1 + 3 * (k2 + k3) + k4) * dt * 0.125      (k4 at t1 itself, not t0 + dt)
+// The output times are the grid, so the solution rows are the step values y1.  f is cfm.py:382-425: CFG with cfg_strength * (1 - t)^2
+// at the STAGE's time, clamped to +-20 -- so time embedding, AdaLN rows and CFG scale are per evaluation.
+static void ode_eval_grid(int method, const std::vector<float>& tg, std::vector<float>& te, std::vector<OdeStage>& st) {
+  const int S = (int)tg.size() - 1;
+  te.clear();
+  st.clear();
+  const float third = 1.0f / 3.0f, two_thirds = 2.0f / 3.0f;
+  for (int k = 0; k < S; ++k) {
+    const float t0 = tg[k], t1 = tg[k + 1], dt = t1 - t0;
+    if (method == 1) {
+      const float half_dt = 0.5f * dt;
+      te.push_back(t0);
+      te.push_back(t0 + half_dt);
+      st.push_back(OdeStage{ODE_MID0, dt, half_dt, 0});
+      st.push_back(OdeStage{ODE_MID1, dt, half_dt, 0});
+    } else {
+      te.push_back(t0);
+      te.push_back(t0 + dt * third);
+      te.push_back(t0 + dt * two_thirds);
+      te.push_back(t1);
+      for (int j = 0; j < 4; ++j) st.push_back(OdeStage{ODE_RK0 + j, dt, 0.f, 0});
+    }
+  }
+}
+
 int lemas_dit::build_tables(const lemas_sample_args* a, hipStream_t s) {
   const int d = cfg.dim;
-  const int Snew = a->steps;
-  std::vector<float> tg(a->t_grid, a->t_grid + Snew + 1);
+  std::vector<float> tg(a->t_grid, a->t_grid + a->steps + 1);
+  // Euler: one evaluation per step at t[k] (the tables below are exactly the ones of the Euler-only engine); otherwise E = S * stages
+  if (ode_method != 0) ode_eval_grid(ode_method, tg, h_te, h_ode);
+  const int Snew = ode_method != 0 ? (int)h_te.size() : a->steps;     // rows of the per-evaluation tables
+  const std::vector<float>& tev = ode_method != 0 ? h_te : tg;        // evaluation k's time: tev[k]
   h_dt.resize(Snew);
   h_cfg.resize(Snew);
   for (int k = 0; k < Snew; ++k) {
-    h_dt[k] = tg[k + 1] - tg[k];                 // torchdiffeq: dt = t1 - t0 in the grid dtype (fp32)
-    const float omt = 1.0f - tg[k];
+    if (ode_method == 0) h_dt[k] = tg[k + 1] - tg[k];                 // torchdiffeq: dt = t1 - t0 in the grid dtype (fp32)
+    else h_dt[k] = h_ode[k].dt;
+    const float omt = 1.0f - tev[k];
     h_cfg[k] = a->cfg_strength * (omt * omt);    // cfm.py:420
   }
   RC_TRY(d_dt.ensure((size_t)Snew * 4));
   RC_TRY(d_cfg.ensure((size_t)Snew * 4));
   HIP_TRY(hipMemcpyAsync(d_dt.p, h_dt.data(), (size_t)Snew * 4, hipMemcpyHostToDevice, s));
   HIP_TRY(hipMemcpyAsync(d_cfg.p, h_cfg.data(), (size_t)Snew * 4, hipMemcpyHostToDevice, s));
+  if (ode_method != 0) {
+    RC_TRY(d_ode.ensure((size_t)Snew * sizeof(OdeStage)));
+    HIP_TRY(hipMemcpyAsync(d_ode.p, h_ode.data(), (size_t)Snew * sizeof(OdeStage), hipMemcpyHostToDevice, s));
+  }
 
-  if (!table_cache || tg != tgrid_cached) {
-    h_t = tg;
+  if (!table_cache || tg != tgrid_cached || tab_method != ode_method) {
+    h_t = tev;
     RC_TRY(d_t.ensure((size_t)(Snew + 1) * 4));
-    HIP_TRY(hipMemcpyAsync(d_t.p, h_t.data(), (size_t)(Snew + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_t.p, h_t.data(), h_t.size() * 4, hipMemcpyHostToDevice, s));
     const int fd = cfg.time_freq_dim;
     RC_TRY(d_sin.ensure((size_t)Snew * fd * 4));
     RC_TRY(d_h1.ensure((size_t)Snew * d * 4));
@@ -610,6 +658,7 @@ int lemas_dit::build_tables(const lemas_sample_args* a, hipStream_t s) {
     HIP_TRY(launch_gemm_f32(F32_BIAS, g, s));
     if (fold_on()) RC_TRY(build_fold_tables(Snew, s));
     tgrid_cached = tg;
+    tab_method = ode_method;
   }
   if (rope_n != a->frames) {
     const int half = cfg.dim_head / 2;
@@ -749,6 +798,7 @@ int lemas_dit::prepare(const lemas_sample_args* a, hipStream_t s) {
 
   if (fp8_wonly) RC_TRY(dequantize_fp8());      // before the tables: the ln-fold rows are sums over the weights the step loop multiplies with
   RC_TRY(build_tables(a, s));
+  E = S * ode_stages(ode_method);
   if (has_len) {
     RC_TRY(d_len.ensure((size_t)B * 4));
     RC_TRY(d_live.ensure((size_t)B * 4));
@@ -803,6 +853,12 @@ int lemas_dit::prepare(const lemas_sample_args* a, hipStream_t s) {
   RC_TRY(d_ff.ensure((size_t)rows * cfg.ff_mult * d * 2));
   RC_TRY(d_cmid.ensure((size_t)rows * d * 2));
   RC_TRY(d_pred.ensure((size_t)rows * md * 4));
+  if (ode_method != 0) RC_TRY(d_ybase.ensure((size_t)B * pitch * md * 4));     // (B and pitch: the 128-row bucket, as d_y)
+  if (ode_method == 2) {
+    RC_TRY(d_k1.ensure((size_t)B * pitch * md * 4));
+    RC_TRY(d_k2.ensure((size_t)B * pitch * md * 4));
+    RC_TRY(d_k3.ensure((size_t)B * pitch * md * 4));
+  }
   RC_TRY(d_lncnt.ensure((size_t)cfg.depth * 2 * 2 * (rows / 64 + 1) * sizeof(unsigned int)));   // >= [block][site][lane][panel of >= 64 rows]
   RC_TRY(d_lnpart.ensure((size_t)rows * (d / 32) * 2 * 4));
   if (fp8) {
@@ -1194,10 +1250,17 @@ int lemas_dit::enqueue_forward(hipStream_t s) {
 }
 
 int lemas_dit::enqueue_update(float* traj, hipStream_t s) {
-  RC_TRY(pbegin(PC_CFG_EULER, s));
-  // traj: caller's dense [S+1, B, N, mel]; the step index is host-known only in the eager path (traj_k)
-  HIP_TRY(launch_cfg_euler(d_y.as<float>(), d_pred.as<float>(), B * pitch, cfg.mel_dim, d_dt.as<float>(), d_cfg.as<float>(),
-                           d_step.as<int>(), nullptr, use_cfg ? 1 : 0, s));
+  // traj: the caller's row of its dense [S+1, B, N, mel] to fill with d_y after this update (eager path, a step's last evaluation only)
+  if (ode_method == 0) {
+    RC_TRY(pbegin(PC_CFG_EULER, s));
+    HIP_TRY(launch_cfg_euler(d_y.as<float>(), d_pred.as<float>(), B * pitch, cfg.mel_dim, d_dt.as<float>(), d_cfg.as<float>(),
+                             d_step.as<int>(), nullptr, use_cfg ? 1 : 0, s));
+  } else {
+    RC_TRY(pbegin(PC_ODE_STAGE, s));
+    HIP_TRY(launch_ode_stage(d_y.as<float>(), d_pred.as<float>(), B * pitch, cfg.mel_dim, d_ode.as<OdeStage>(), d_cfg.as<float>(),
+                             d_step.as<int>(), d_ybase.as<float>(), d_k1.as<float>(), d_k2.as<float>(), d_k3.as<float>(), use_cfg ? 1 : 0,
+                             n_cus, s));
+  }
   RC_TRY(pend(s));
   if (traj) {
     const size_t w = (size_t)N * cfg.mel_dim * 4;
@@ -1206,7 +1269,7 @@ int lemas_dit::enqueue_update(float* traj, hipStream_t s) {
   return 0;
 }
 
-// one ODE step (DiT forward of both CFG branches + CFG / clamp / Euler update) captured from stream s
+// one ODE evaluation (DiT forward of both CFG branches + CFG / clamp / Euler update or solver stage) captured from stream s
 int lemas_dit::capture_step(hipStream_t s, hipGraph_t* out) {
   hipGraph_t graph = nullptr;
   HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
@@ -1228,9 +1291,10 @@ int lemas_dit::step_graph(hipStream_t s, hipGraphExec_t* exec, hipEvent_t* done)
     drop_graphs();
     graph_generation = moved;
   }
-  char key[112];
-  snprintf(key, sizeof key, "B%d_P%d_cfg%d_len%d_dual%d_f8%d_ln%d_av%d", B, pitch, (int)use_cfg, (int)has_len, dual ? lanes_for(s) : 0, fp8 ? 16 + fp8_sites() : fp8_wonly ? 2 : 0,
-           (int)ln_fused + 2 * (int)fold_on(), attn_variant);
+  char key[128];
+  int kn = snprintf(key, sizeof key, "B%d_P%d_cfg%d_len%d_dual%d_f8%d_ln%d_av%d", B, pitch, (int)use_cfg, (int)has_len, dual ? lanes_for(s) : 0,
+                    fp8 ? 16 + fp8_sites() : fp8_wonly ? 2 : 0, (int)ln_fused + 2 * (int)fold_on(), attn_variant);
+  if (ode_method != 0 && kn > 0 && kn < (int)sizeof key) snprintf(key + kn, sizeof key - kn, "_ode%d", ode_method);   // (Euler's key as before)
   auto it = graphs.find(key);
   if (it == graphs.end()) {
     while ((int)graphs.size() >= (graph_cap > 0 ? graph_cap : 1)) {       // evict the least recently used bucket
@@ -1305,14 +1369,17 @@ int lemas_dit::solve(const lemas_sample_args* a, hipStream_t s) {
     // `done` fences this graph's launches for a later hipGraphExecUpdate / destroy: recorded also when a launch fails mid-loop, so that a
     // graph whose earlier launches are still running is never patched or destroyed under them
     hipError_t el = hipSuccess;
-    for (int k = 0; k < S && el == hipSuccess; ++k) el = hipGraphLaunch(exec, s);
+    for (int k = 0; k < E && el == hipSuccess; ++k) el = hipGraphLaunch(exec, s);    // one launch per evaluation
     const hipError_t er = hipEventRecord(done, s);
     HIP_TRY(el);
     HIP_TRY(er);
   } else {
-    for (int k = 0; k < S; ++k) {
+    const int ns = ode_stages(ode_method);
+    for (int e = 0; e < E; ++e) {
+      const int k = e / ns;
+      const bool last = e % ns == ns - 1;       // the trajectory holds one row per STEP: written after a step's last stage
       RC_TRY(enqueue_forward(s));
-      RC_TRY(enqueue_update(a->trajectory ? a->trajectory + (size_t)(k + 1) * B * N * cfg.mel_dim : nullptr, s));
+      RC_TRY(enqueue_update(a->trajectory && last ? a->trajectory + (size_t)(k + 1) * B * N * cfg.mel_dim : nullptr, s));
     }
   }
   HIP_TRY(hipMemcpy2DAsync(a->y, yw, d_y.p, ypitch, yw, B, hipMemcpyDeviceToDevice, s));
@@ -1453,6 +1520,16 @@ int lemas_dit_set_option(lemas_dit* m, const char* key, int64_t value) {
     m->fp8_wonly = value == 2;
     return 0;
   }
+  if (!strcmp(key, "ode_method")) {   // 0 euler, 1 midpoint, 2 rk4; takes effect at the next prepare()
+    if (value < 0 || value > 2) { set_error("lemas_dit_set_option: ode_method is 0 (euler), 1 (midpoint) or 2 (rk4)"); return LEMAS_E_ARG; }
+    if (m->ode_method != (int)value) {
+      // the prepared tables, counter range and stage buffers belong to the old method: solve() / forward() refuse until prepare() runs again
+      m->ode_method = (int)value;
+      m->prepared = false;
+      m->drop_graphs();
+    }
+    return 0;
+  }
   if (!strcmp(key, "graph_cache")) {
     if (value < 1 || value > 1024) { set_error("lemas_dit_set_option: graph_cache is the number of step-graph buckets kept, 1 .. 1024"); return LEMAS_E_ARG; }
     m->graph_cap = (int)value;
@@ -1517,7 +1594,10 @@ int lemas_dit_sample(lemas_dit* m, const lemas_sample_args* a, void* stream) {
 int lemas_dit_forward(lemas_dit* m, const float* x, int32_t step_index, float* pred, void* stream) {
   if (!m || !x || !pred) return LEMAS_E_ARG;
   if (!m->finalized || !m->prepared) { set_error("lemas_dit_forward: prepare() has not run on the finalized weights"); return LEMAS_E_STATE; }
-  if (step_index < 0 || step_index >= m->S) { set_error("lemas_dit_forward: step index out of range"); return LEMAS_E_ARG; }
+  if (step_index < 0 || step_index >= m->E) {
+    set_error("lemas_dit_forward: evaluation index %d outside [0, %d) (steps x stages of the prepared ode_method)", (int)step_index, m->E);
+    return LEMAS_E_ARG;
+  }
   hipStream_t s = (hipStream_t)stream;
   const size_t w = (size_t)m->N * m->cfg.mel_dim * 4, wp = (size_t)m->pitch * m->cfg.mel_dim * 4;
   HIP_TRY(hipMemsetAsync(m->d_y.p, 0, (size_t)m->B * wp, s));

@@ -1,6 +1,7 @@
 // HBM-bound row/elementwise kernels of the DiT step loop and its per-utterance setup (gfx950).
 //   ln_mod        modules.py:314,637 / :335  LayerNorm(no affine, eps 1e-6) * (1 + scale) + shift  -> bf16
 //   cfg_euler     cfm.py:420-424 + the Euler update of torchdiffeq (call site cfm.py:456)
+//   ode_stage     the same CFG + clamp, then one stage of torchdiffeq's fixed-grid midpoint / rk4 (option "ode_method")
 //   rope_table    x_transformers RotaryEmbedding.forward_from_seq_len (call site dit.py:236)
 //   misc          fp32->bf16 conversion / weight re-layout used when weights are loaded
 #include "common.h"
@@ -279,6 +280,80 @@ __global__ __launch_bounds__(256) void cfg_euler_kernel(float* __restrict__ y, c
   }
 }
 
+// one STAGE of a higher-order fixed-grid solver (torchdiffeq 0.2.4 fixed_grid.Midpoint / rk_common.rk4_alt_step_func, dt = t1 - t0,
+// y1 = y0 + dy), with the CFG + clamp of cfm.py:420-424 at the stage's own time (cfg_tab is per EVALUATION).  The evaluation counter
+// selects the stage's row of `stages`: its kind and dt.  Buffers: base = y0 of the step, k1..k3 = the rk4 slopes; y = the next stage's
+// input, or y1 at the step's last stage.  Products and sums are rounded one by one in torch's order (no FMA contraction), so the
+// solve equals the same solver composed on the host from single forwards (tests/test_gpu_16_ode_methods.py):
+//   MID0   f0 = f(t0, y0):               base = y0;  y = y0 + f0 * half_dt          (c = half_dt = 0.5 * dt)
+//   MID1   f1 = f(t0 + half_dt, y_mid):  y = y0 + dt * f1
+//   RK0    k1 = f(t0, y0):               base = y0;  k1;  y = y0 + dt * k1 * (1/3)
+//   RK1    k2 = f(t0 + dt/3, .):         k2;  y = y0 + dt * (k2 - k1 * (1/3))
+//   RK2    k3 = f(t0 + 2 dt/3, .):       k3;  y = y0 + dt * (k1 - k2 + k3)
+//   RK3    k4 = f(t1, .):                y = y0 + (k1 + 3 * (k2 + k3) + k4) * dt * 0.125
+// A product that no FMA can absorb: HIP's __fmul_rn is a plain `*`, and under this build's -O3 contraction (which ignores
+// `#pragma clang fp contract`) `a * b + c` becomes one v_fma -- one ulp of difference in a stage input then flips bf16 roundings of
+// the next network evaluation.  The empty asm makes the rounded product opaque to the combiner; the add after it stays an add.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+  float p = a * b;
+  __asm__ volatile("" : "+v"(p));
+  return p;
+}
+
+__device__ __forceinline__ float ode_cfg(float pc, float pu, float cg) {
+  return fminf(fmaxf(pc + mul_rn(pc - pu, cg), -20.0f), 20.0f);
+}
+
+__device__ __forceinline__ float ode_stage_elem(int kind, float dt, float c, float f, float y0, float a1, float a2, float a3) {
+  const float third = 1.0f / 3.0f;
+  switch (kind) {
+    case ODE_MID0: return y0 + mul_rn(f, c);
+    case ODE_MID1: return y0 + mul_rn(dt, f);
+    case ODE_RK0: return y0 + mul_rn(mul_rn(dt, f), third);
+    case ODE_RK1: return y0 + mul_rn(dt, f - mul_rn(a1, third));
+    case ODE_RK2: return y0 + mul_rn(dt, (a1 - a2) + f);
+    default: return y0 + mul_rn(mul_rn((a1 + mul_rn(3.0f, a2 + a3)) + f, dt), 0.125f);
+  }
+}
+
+// float4 per thread over B*pitch*mel (a multiple of 4: pitch is a multiple of 128), grid-stride over a grid sized to the CUs.  The stage
+// kind is uniform over the launch: each stage touches only the buffers it needs (rk4's last stage: pred x 2, base, k1..k3 in, y out)
+__global__ __launch_bounds__(256) void ode_stage_kernel(float* __restrict__ y, const float* __restrict__ pred, size_t total4,
+                                                        const OdeStage* __restrict__ stages, const float* __restrict__ cfg_tab,
+                                                        const int* __restrict__ step_idx, float* __restrict__ base, float* __restrict__ k1,
+                                                        float* __restrict__ k2, float* __restrict__ k3, int use_cfg) {
+  const int e = step_idx[0];
+  const OdeStage st = stages[e];
+  const float cg = cfg_tab[e];
+  const int kind = st.kind;
+  const bool first = kind == ODE_MID0 || kind == ODE_RK0;
+  float4* Y = reinterpret_cast<float4*>(y);
+  float4* B0 = reinterpret_cast<float4*>(base);
+  float4* K1 = reinterpret_cast<float4*>(k1);
+  float4* K2 = reinterpret_cast<float4*>(k2);
+  float4* K3 = reinterpret_cast<float4*>(k3);
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (size_t v = blockIdx.x * (size_t)blockDim.x + threadIdx.x; v < total4; v += (size_t)gridDim.x * blockDim.x) {
+    const float4 pc = reinterpret_cast<const float4*>(pred)[v];
+    float4 f = pc;
+    if (use_cfg) {
+      const float4 pu = reinterpret_cast<const float4*>(pred)[total4 + v];
+      f = make_float4(ode_cfg(pc.x, pu.x, cg), ode_cfg(pc.y, pu.y, cg), ode_cfg(pc.z, pu.z, cg), ode_cfg(pc.w, pu.w, cg));
+    }
+    float4 y0;
+    if (first) { y0 = Y[v]; B0[v] = y0; }
+    else y0 = B0[v];
+    const float4 a1 = kind >= ODE_RK1 ? K1[v] : z;
+    const float4 a2 = kind >= ODE_RK2 ? K2[v] : z;
+    const float4 a3 = kind >= ODE_RK3 ? K3[v] : z;
+    if (kind == ODE_RK0) K1[v] = f;
+    else if (kind == ODE_RK1) K2[v] = f;
+    else if (kind == ODE_RK2) K3[v] = f;
+    Y[v] = make_float4(ode_stage_elem(kind, st.dt, st.c, f.x, y0.x, a1.x, a2.x, a3.x), ode_stage_elem(kind, st.dt, st.c, f.y, y0.y, a1.y, a2.y, a3.y),
+                       ode_stage_elem(kind, st.dt, st.c, f.z, y0.z, a1.z, a2.z, a3.z), ode_stage_elem(kind, st.dt, st.c, f.w, y0.w, a1.w, a2.w, a3.w));
+  }
+}
+
 // the step counter is advanced by its own 1-thread kernel so that every kernel of step k reads the same value
 __global__ void step_advance_kernel(int* step_idx, int value, int set) { step_idx[0] = set ? value : step_idx[0] + 1; }
 
@@ -385,6 +460,17 @@ hipError_t launch_cfg_euler(float* y, const float* pred, int rows, int cols, con
                             int* step_idx, float* traj, int use_cfg, hipStream_t s) {
   hipLaunchKernelGGL(cfg_euler_kernel, dim3(grid_for((size_t)rows * cols)), dim3(256), 0, s, y, pred, rows, cols, dt_tab,
                      cfg_tab, step_idx, traj, use_cfg);
+  hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, step_idx, 0, 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_ode_stage(float* y, const float* pred, int rows, int cols, const OdeStage* stages, const float* cfg_tab, int* step_idx,
+                            float* base, float* k1, float* k2, float* k3, int use_cfg, int n_cus, hipStream_t s) {
+  const size_t total = (size_t)rows * cols;
+  if (total % 4 != 0 || !base) return hipErrorInvalidValue;
+  const size_t total4 = total / 4, need = (total4 + 255) / 256, cap = (size_t)(n_cus > 0 ? n_cus : 256) * 2;
+  const int grid = (int)(need < cap ? (need ? need : 1) : cap);
+  hipLaunchKernelGGL(ode_stage_kernel, dim3(grid), dim3(256), 0, s, y, pred, total4, stages, cfg_tab, step_idx, base, k1, k2, k3, use_cfg);
   hipLaunchKernelGGL(step_advance_kernel, dim3(1), dim3(1), 0, s, step_idx, 0, 0);
   return hipGetLastError();
 }

@@ -204,7 +204,9 @@ class DiTEngine(_Streamed):
         return out, y
 
     def forward(self, x, step_index: int):
-        """One DiT forward (both CFG branches) at step ``step_index`` of the prepared grid -> [BB, N, mel]."""
+        """One DiT forward (both CFG branches) at EVALUATION ``step_index`` of the prepared grid -> [BB, N, mel]: with option
+        "ode_method" 0 (euler) evaluation k is step k at t[k]; with midpoint / rk4 it is stage k % stages (2 / 4) of step k // stages,
+        at the stage's time (``model.cfm.ode_eval_times``), in [0, steps * stages)."""
         cond, cond_mask = self._prep_keep[0], self._prep_keep[1]
         B, N = cond_mask.shape          # cond may hold fewer rows than N (cond_rows): the library works on N = frames
         md = cond.shape[2]

@@ -22,7 +22,7 @@ import torch
 import yaml
 
 from ..engine import VocosEngine
-from ..model.cfm import CFM, pad_rows
+from ..model.cfm import CFM, ode_method_code, pad_rows
 from ..model.layout import DROPPED_ON_LOAD, DiTArch, VocosArch
 
 # module-level defaults of the reference (:68-81)
@@ -129,6 +129,7 @@ def load_model(model_cls, model_cfg, ckpt_path, mel_spec_type=mel_spec_type, voc
                state_dict: Optional[dict] = None, vocab_char_map: Optional[dict] = None):
     """``model_cls`` is accepted for signature parity (the reference passes ``DiT``); ``model_cfg`` is ``model.arch``
     of the yaml.  ``state_dict`` + ``vocab_char_map`` bypass the files (synthetic weights)."""
+    ode_method_code(dict(method=ode_method))         # euler / midpoint / rk4 (CFM refuses the rest; checked before any file is read)
     arch = DiTArch.from_yaml_arch(dict(model_cfg))
     if vocab_char_map is None:
         if vocab_file == "":

@@ -3,8 +3,9 @@
 Same constructor role and the same ``sample(...)`` signature, argument meaning, defaults and error
 behaviour as ``lemas_tts/model/cfm.py:206-227``; the body only does the integer/boolean bookkeeping
 of ``cfm.py:284-339`` (token ids, lengths, masks, duration) and the t-grid (``:445-453``) on the
-host, then hands the batch to the MI355X engine, which runs the hoists, the NFE-step Euler loop with
-CFG folded into the batch, and the final ``where``.  There is no CPU path.
+host, then hands the batch to the MI355X engine, which runs the hoists, the NFE-step ODE loop with
+CFG folded into the batch, and the final ``where``.  There is no CPU path.  The solver is torchdiffeq's fixed-grid
+``euler`` (the reference's default), ``midpoint`` or ``rk4`` (``odeint_kwargs=dict(method=...)``, cfm.py:93,456).
 """
 from __future__ import annotations
 
@@ -92,6 +93,40 @@ def time_grid(steps: int, sway_sampling_coef, t_start: float = 0.0) -> torch.Ten
     return t ** (1 + sway_max)
 
 
+# odeint_kwargs["method"] -> engine option "ode_method"; network evaluations per ODE step
+ODE_METHODS = {"euler": 0, "midpoint": 1, "rk4": 2}
+ODE_STAGES = {"euler": 1, "midpoint": 2, "rk4": 4}
+
+
+def ode_method_code(odeint_kwargs: dict) -> int:
+    """The engine's code for ``odeint_kwargs["method"]``; anything but the three fixed-grid solvers is refused."""
+    m = odeint_kwargs.get("method", "euler")
+    if m not in ODE_METHODS:
+        raise NotImplementedError(f"odeint method {m!r} is not built: the supported fixed-grid solvers are "
+                                  f"{', '.join(ODE_METHODS)} (adaptive and multistep solvers such as dopri5 / explicit_adams are not)")
+    return ODE_METHODS[m]
+
+
+def ode_eval_times(t: torch.Tensor, method: str) -> torch.Tensor:
+    """Times of the network evaluations of one fixed-grid solve on grid ``t`` (fp32), in order -- what the engine's tables are built
+    over (csrc/engine_dit.hip ode_eval_grid).  torchdiffeq 0.2.4, dt = t1 - t0 per step: euler t0; midpoint t0, t0 + 0.5 * dt; rk4 (3/8
+    rule) t0, t0 + dt * (1/3), t0 + dt * (2/3), t1."""
+    t = t.to(torch.float32)
+    out = []
+    for k in range(t.shape[0] - 1):
+        t0, t1 = t[k], t[k + 1]
+        dt = t1 - t0
+        if method == "euler":
+            out += [t0]
+        elif method == "midpoint":
+            out += [t0, t0 + 0.5 * dt]
+        elif method == "rk4":
+            out += [t0, t0 + dt * (1.0 / 3.0), t0 + dt * (2.0 / 3.0), t1]
+        else:
+            raise NotImplementedError(method)
+    return torch.stack(out)
+
+
 class CFM:
     """Inference-time stand-in for ``lemas_tts.model.cfm.CFM``: ``transformer`` is the weight holder
     (arch + state dict) and the compute lives in a :class:`DiTEngine`."""
@@ -100,8 +135,7 @@ class CFM:
                  device="cuda:0", use_prosody_encoder: bool = False, num_channels: int = 100,
                  odeint_kwargs: dict = dict(method="euler"), mel_spec_module=None, fp8_weights: bool = False,
                  prosody_encoder=None):
-        if odeint_kwargs.get("method", "euler") != "euler":
-            raise NotImplementedError("only the fixed-grid Euler solver of the shipped configs is built")
+        ode_method_code(odeint_kwargs)
         self.arch = arch
         self.num_channels = num_channels
         self.vocab_char_map = vocab_char_map
@@ -227,6 +261,8 @@ class CFM:
         # what the engine was handed, for measurement tools that time its prepare() / solve() halves on the same inputs (bench.py)
         self.last_engine_call = dict(cond=cond, cond_mask=cond_mask, text=text, t_grid=t.numpy(), y0=y0, cond_frames=min(cond_seq_len, n),
                                      cfg_strength=float(cfg_strength), seq_len=seq_len, prosody=pros)
+        # the solver: an engine option that takes effect at its next prepare (a change drops the prepared state; a repeat is free)
+        self.engine.set_option("ode_method", ode_method_code(self.odeint_kwargs))
         out, y_final, traj = self.engine.sample(
             cond, cond_mask, text, t.numpy(), y0, cond_frames=min(cond_seq_len, n), cfg_strength=float(cfg_strength),   # F.pad above CROPS the
             # prompt when `lens` lets the duration fall below the prompt length (negative pad, as cfm.py:311 does)
